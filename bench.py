@@ -11,6 +11,10 @@ sides; elapsed = MAX over ranks; rank 0 prints ONE JSON line.
 owns its full batch; the only cross-worker exchange is the outer
 pseudo-gradient all-reduce every H steps, reported as outer_sync_fraction).
 Inputs are pre-generated on device before the timed region.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+as float32 .npy files (see _dump_outputs), so two builds can be compared
+output for output on identical seeded inputs.
 """
 
 from __future__ import annotations
@@ -62,6 +66,10 @@ def main():
                     help="skip the in-process roofline/MFMA-fraction measurements "
                          "(for clean rocprofv3 kernel traces of the step alone)")
     ap.add_argument("--cpu-baseline-only", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs "
+                         "(micro-batch losses, grad norm, seeded sample of the "
+                         "updated parameters) to DIR/<name>.npy")
     ap.add_argument("--advance-steps", type=int, default=0,
                     help="pre-advance the DiLoCo progress tracker by N inner steps "
                          "(no compute) so a short timed window can cross an outer "
@@ -69,6 +77,8 @@ def main():
                          "--warmup 2 --steps 6 times steps 500-505 incl. the outer "
                          "round at 500 (the H=500 sustained leg)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     dist = _dist_init()
     rank = dist.get_rank() if dist else 0
@@ -126,17 +136,22 @@ def main():
                    if os.environ.get("DK_MAIN_PRIO", "1") != "0" else None)
 
     def one_step():
+        """One inner step; returns the per-micro-batch losses and the
+        pre-clip grad norm (device tensors, no host sync)."""
         import contextlib
 
+        losses = []
         with torch.cuda.stream(main_stream) if main_stream else contextlib.nullcontext():
             for mb in micros:
-                loss = model(**mb).loss / grad_acc
-                loss.backward()
-            clip_grad_norm_flat_(opt.flat.flat_grad, 1.0)
+                loss = model(**mb).loss
+                losses.append(loss.detach())
+                (loss / grad_acc).backward()
+            grad_norm = clip_grad_norm_flat_(opt.flat.flat_grad, 1.0)
             opt.step()
             opt.zero_grad()
         if main_stream:
             torch.cuda.current_stream().wait_stream(main_stream)
+        return losses, grad_norm
 
     if args.advance_steps:
         # tracker-only advance: the inner steps are identical regardless of
@@ -153,11 +168,16 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        step_out = one_step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    # before the outer-round and roofline measurements below touch the params
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, *step_out, opt.flat.flat_param)
+
     if dist:
         t = torch.tensor([elapsed], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -264,6 +284,39 @@ def main():
     if dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_PARAM_SAMPLES = 1 << 22  # 16 MB of fp32; the dump cap is 64 MB
+
+
+def _dump_outputs(out_dir, losses, grad_norm, flat_param) -> None:
+    """Write the last timed step's outputs as float32 .npy files:
+
+      loss.npy       [grad_acc]  each micro-batch's mean CE loss (unscaled)
+      grad_norm.npy  [1]         global L2 grad norm before clipping
+      params.npy     [<= 4M]     the updated fp32 master parameters; all of
+                                 them when they fit, else a fixed sample at
+                                 sorted indices drawn from a seed-0 CPU
+                                 generator (same indices on every run)
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = flat_param.numel()
+    if n <= DUMP_PARAM_SAMPLES:
+        params = flat_param
+    else:
+        gen = torch.Generator(device="cpu").manual_seed(0)
+        idx = torch.randint(0, n, (DUMP_PARAM_SAMPLES,), generator=gen).sort().values
+        params = flat_param[idx.to(flat_param.device)]
+    arrays = {
+        "loss": torch.stack(losses),
+        "grad_norm": grad_norm.reshape(1),
+        "params": params,
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                t.detach().float().cpu().numpy())
 
 
 def _mfma_fractions(args, mcfg) -> dict:

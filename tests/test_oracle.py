@@ -37,13 +37,26 @@ def test_oracle_matches_golden(golden_dir, fixture_2m, name):
     assert result["outer_steps"] == golden["outer_steps"]
 
 
+@pytest.fixture
+def reference_thread_count():
+    """The reference traces were recorded with 4 intra-op threads
+    (oracle/run_reference.py sets OMP_NUM_THREADS=4).  fp32 CPU GEMM
+    reduction order follows the thread count, so a bit-equal re-run must use
+    the same count rather than whatever the host's core count gives."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(4)
+    yield
+    torch.set_num_threads(prev)
+
+
 @pytest.mark.parametrize("trace_name,n_workers,local_steps", [
     ("reference_trace_w1_h1", 1, 1),
     ("reference_trace_w2_h3", 2, 3),
     ("reference_trace_w2_h5_seq1024", 2, 5),  # the reference's e2e test shape
 ])
 def test_oracle_matches_reference_executed_trace(golden_dir, fixture_2m, trace_name,
-                                                 n_workers, local_steps):
+                                                 n_workers, local_steps,
+                                                 reference_thread_count):
     """THE parity pin: the oracle restatement must reproduce
     the trace of the reference's OWN train_diloco_torch.py, executed by
     oracle/run_reference.py (the loop's actual lines, exec'd on gloo CPU with

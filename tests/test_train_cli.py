@@ -25,6 +25,15 @@ def get_random_available_port():
         return s.getsockname()[1]
 
 
+def _cli_env(repo_root):
+    env = dict(os.environ)
+    env["PYTHONPATH"] = repo_root + os.pathsep + env.get("PYTHONPATH", "")
+    # the CPU/gloo path under test, also on a GPU host: the CLI picks cuda
+    # whenever a device is visible, and a 1-GPU host has no device for rank 1
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    return env
+
+
 def _run_cli(repo_root, nproc, extra, timeout=900):
     cmd = [
         sys.executable, "-m", "torch.distributed.run",
@@ -32,8 +41,7 @@ def _run_cli(repo_root, nproc, extra, timeout=900):
         f"127.0.0.1:{get_random_available_port()}", "--master-addr", "127.0.0.1",
         "-m", "opendiloco_amd.train_fsdp", *extra,
     ]
-    env = dict(os.environ)
-    env["PYTHONPATH"] = repo_root + os.pathsep + env.get("PYTHONPATH", "")
+    env = _cli_env(repo_root)
     r = subprocess.run(cmd, cwd=repo_root, env=env, timeout=timeout,
                        capture_output=True, text=True)
     if r.returncode != 0:
@@ -141,8 +149,7 @@ def test_rank_drop_fails_fast(base_config, repo_root, tmp_path):
         "--hv.fail_rank_drop", "--max_steps", "6",
         "--project", str(tmp_path / "log.pkl"),
     ]
-    env = dict(os.environ)
-    env["PYTHONPATH"] = repo_root + os.pathsep + env.get("PYTHONPATH", "")
+    env = _cli_env(repo_root)
     env["DILOCO_TEST_DIE_RANK_STEP"] = "1:2"  # rank 1 dies after step 2 (< H)
     env["GLOO_SOCKET_IFNAME"] = env.get("GLOO_SOCKET_IFNAME", "lo")
     r = subprocess.run(cmd, cwd=repo_root, env=env, timeout=600,
