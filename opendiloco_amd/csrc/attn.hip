@@ -14,9 +14,10 @@
 //    running (m, l) per row, wave-shuffle row reductions (no serial lanes);
 //    P goes through a small per-wave LDS tile to re-shape C-layout ->
 //    A-layout.  lse = m + log(l) saved for backward.
-//  - backward: split into a dK/dV kernel (grid over kv tiles; P^T recomputed
-//    from lse) and a dQ kernel (grid over q tiles) — no atomics anywhere, so
-//    gradients are bit-deterministic run to run (the reference's tests
+//  - backward: split into a dK/dV kernel (grid over kv tiles, key on the
+//    MFMA lane) and a dQ kernel (grid over q tiles, query on the lane);
+//    P/dS recomputed from lse and kept in registers — no atomics anywhere,
+//    so gradients are bit-deterministic run to run (the reference's tests
 //    compare loss traces, test_train.py:82).  GQA handled by writing dK/dV
 //    per q-head; the caller sums the group (ratio == 1 writes directly).
 //
@@ -350,6 +351,44 @@ __device__ __forceinline__ typename MFMA32<DT>::frag trread_afrag32(
   return f;
 }
 
+// Pack rows 16c .. 16c+15 of a 32x32 f32 accumulator X (C map: col = l&31,
+// row = (r&3) + 8*(r>>2) + 4*(l>>5)) into a 32x32x16 fragment in natural k
+// order: element j of lane half h = X[16c + 8h + j][l&31] — the B operand of
+// A·X (or the A operand of X^T·B).  Registers 8c..8c+7 hold rows
+// {0..3, 8..11} + 4h of the chunk; cvt_pk pairs them as w0=(0,1) w1=(2,3)
+// w2=(8,9) w3=(10,11) (+4 in the high half), and swap(w0,w2) ->
+// dwords {0, 2}, swap(w1,w3) -> {1, 3} regroups them (hardware-verified by
+// dk_probe_mfma_32x32x16 and dk_probe_permlane32).
+template <int DT> struct Pack2;
+template <> struct Pack2<2> { typedef __attribute__((ext_vector_type(2))) __bf16 V; };
+template <> struct Pack2<1> { typedef __attribute__((ext_vector_type(2))) _Float16 V; };
+// two f32 -> one packed 16-bit dword: a single v_cvt_pk_{bf16,f16}_f32 (RTNE)
+template <int DT>
+__device__ __forceinline__ unsigned cvt_pk2(float a, float b) {
+  typedef __attribute__((ext_vector_type(2))) float f2;
+  typename Pack2<DT>::V r = __builtin_convertvector((f2){a, b}, typename Pack2<DT>::V);
+  unsigned u;
+  __builtin_memcpy(&u, &r, 4);
+  return u;
+}
+
+template <int DT>
+__device__ __forceinline__ typename MFMA32<DT>::frag pack_frag32(const floatx16& x, int c) {
+  const int base = c * 8;
+  const unsigned w0 = cvt_pk2<DT>(x[base + 0], x[base + 1]);
+  const unsigned w1 = cvt_pk2<DT>(x[base + 2], x[base + 3]);
+  const unsigned w2 = cvt_pk2<DT>(x[base + 4], x[base + 5]);
+  const unsigned w3 = cvt_pk2<DT>(x[base + 6], x[base + 7]);
+  auto s0 = __builtin_amdgcn_permlane32_swap((int)w0, (int)w2, false, false);
+  auto s1 = __builtin_amdgcn_permlane32_swap((int)w1, (int)w3, false, false);
+  intx4 pw;
+  pw[0] = s0[0];
+  pw[1] = s1[0];
+  pw[2] = s0[1];
+  pw[3] = s1[1];
+  return *(typename MFMA32<DT>::frag*)&pw;
+}
+
 template <int DT, int D>
 __global__ __launch_bounds__(256, 4) void attn_fwd_v3_kernel(
     typename DTraits<DT>::T* __restrict__ o, float* __restrict__ lse,
@@ -496,33 +535,10 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_v3_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[mt][r] *= alpha;
 
-      // ---- pack P into PV B-fragments via cvt_pk + permlane32_swap ----
-      // chunk c covers keys sbase + c*16 .. +15; per chunk the four packed
-      // words are w0=(k0,k1) w1=(k2,k3) w2=(k8,k9) w3=(k10,k11) in the low
-      // half (+4 in the high half); swap(w0,w2) -> frag dwords {d0, d2},
-      // swap(w1,w3) -> {d1, d3}  (hardware-verified regrouping).
-      auto bits = [](T t) -> unsigned {
-        unsigned short u;
-        __builtin_memcpy(&u, &t, 2);
-        return (unsigned)u;
-      };
+      // ---- pack P into PV B-fragments (chunk c = keys sbase + c*16 ..) ----
       frag pfrag[2];
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int base = c * 8;
-        unsigned w0 = bits(TR::fromF(sc[base + 0])) | (bits(TR::fromF(sc[base + 1])) << 16);
-        unsigned w1 = bits(TR::fromF(sc[base + 2])) | (bits(TR::fromF(sc[base + 3])) << 16);
-        unsigned w2 = bits(TR::fromF(sc[base + 4])) | (bits(TR::fromF(sc[base + 5])) << 16);
-        unsigned w3 = bits(TR::fromF(sc[base + 6])) | (bits(TR::fromF(sc[base + 7])) << 16);
-        auto s0 = __builtin_amdgcn_permlane32_swap((int)w0, (int)w2, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap((int)w1, (int)w3, false, false);
-        intx4 pw;
-        pw[0] = s0[0];
-        pw[1] = s1[0];
-        pw[2] = s0[1];
-        pw[3] = s1[1];
-        pfrag[c] = *(frag*)&pw;
-      }
+      for (int c = 0; c < 2; ++c) pfrag[c] = pack_frag32<DT>(sc, c);
 
       // ---- O^T += V^T P  (A = V^T tr_read from row-major V, B = P) ----
       __builtin_amdgcn_s_setprio(1);
@@ -597,240 +613,40 @@ __global__ void attn_bwd_pre_kernel(float* __restrict__ delta,
   }
 }
 
-// ======================= bwd dK/dV =======================
-// grid over (b, hq, kv-tile of 128 keys); 8 waves x 16 keys each.  Loop q
-// tiles of 32 with double-buffered async staging (v2 structure); dV/dK
-// B-fragments tr_read straight from the row-major Q/dO images.
-// LDS: Q[2][32][D+8] | dO[2][32][D+8] | lse[2][32] f32 | delta[2][32] f32 |
-//      P_T[8][16][32+8] | dS[8][16][32+8]   (dV/dK B-frags come straight
-//      from the row-major Q/dO images via ds_read_b64_tr_b16)
-template <int DT, int D>
-__global__ __launch_bounds__(512) void attn_bwd_dkdv_kernel(
-    typename DTraits<DT>::T* __restrict__ dk_out,
-    typename DTraits<DT>::T* __restrict__ dv_out,
-    const typename DTraits<DT>::T* __restrict__ do_,
-    const typename DTraits<DT>::T* __restrict__ q,
-    const typename DTraits<DT>::T* __restrict__ k,
-    const typename DTraits<DT>::T* __restrict__ v,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    int B, int Hq, int Hkv, int S, float scale,
-    int64_t g_sb, int64_t g_sh, int64_t g_sr,
-    int64_t v_sb, int64_t v_sh, int64_t v_sr,
-    int64_t dv_sb, int64_t dv_sh, int64_t dv_sr) {
-  using TR = DTraits<DT>;
-  using T = typename TR::T;
-  using MF = MFMA16<DT>;
-  using frag = typename MF::frag;
-  constexpr int QT = 32;                     // compute half-tile (q rows)
-  constexpr int QTT = 64;                    // staged tile: 2 halves / barrier
-  constexpr int QS = QT + 8;
-  constexpr int DS = D + 8;
-  constexpr int NKC = D / 32;
-  constexpr int NDN = D / 16;
+// ======================= bwd: key/query on the lane, 32x32x16 tiles =======================
+// Both backward kernels orient every score tile so the accumulator of S and
+// dP is already the B operand of the product that follows it (guide
+// Appendix B "Key on the lane"): pack_frag32 (cvt_pk + permlane32_swap)
+// turns the f32 tile into bf16/f16 fragments in registers, so neither
+// kernel writes P or dS to LDS.  Row constants ride in the accumulators:
+// S starts at -lse/scale, so p = exp2(S * scale*log2(e)) is one multiply and
+// one v_exp; dP starts at -delta, so dS = p * dP is one multiply.  scale is
+// applied once to dQ / dK in the epilogue.  The causal mask runs only on the
+// diagonal tile (and the <S bound only on the last), chosen wave-uniformly,
+// so off-diagonal tiles carry no compares.  No atomics: every output element
+// is written by exactly one lane (bit-deterministic run to run).
 
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Q_lds = (T*)smem_raw;                   // [2][QTT][DS]
-  T* dO_lds = Q_lds + 2 * QTT * DS;          // [2][QTT][DS]
-  T* PT_lds = dO_lds + 2 * QTT * DS;         // [8][16][QS]  (P^T tiles)
-  T* DS_lds = PT_lds + 8 * 16 * QS;          // [8][16][QS]  (dS^T tiles; separate
-                                             //  buffer: avoids an LDS WAR hazard
-                                             //  between the P^T A-frag read and
-                                             //  the dS^T writes in one iteration)
-  float* lse_lds = (float*)(DS_lds + 8 * 16 * QS);  // [2][QTT]
-  float* dl_lds = lse_lds + 2 * QTT;                // [2][QTT]
+__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int lo = lane & 15;
-  const int hi = lane >> 4;
-
-  const int nKT = (S + 127) / 128;           // 8 waves x 16 keys per WG
-  int bid = blockIdx.x;
-  const int kt = bid % nKT;
-  const int h = (bid / nKT) % Hq;
-  const int b = bid / (nKT * Hq);
-  const int hkv = h / (Hq / Hkv);
-
-  const int k0 = kt * 128 + wave * 16;       // this wave's first key
-  const int64_t qoff = (((int64_t)b * Hq + h) * S) * D;
-  const int64_t kvoff = (((int64_t)b * Hkv + hkv) * S) * D;
-  const int64_t lseoff = ((int64_t)b * Hq + h) * S;
-  const int64_t voff = v_sb ? ((int64_t)b * v_sb + (int64_t)hkv * v_sh) : kvoff;
-  const int64_t v_rs = v_sb ? v_sr : (int64_t)D;
-
-  // K,V A-fragments for this wave's 16 keys
-  frag k_frag[NKC], v_frag[NKC];
-  {
-    const int krow = k0 + lo;
-    const int kr_c = krow < S ? krow : S - 1;
+// 8-byte store of four consecutive f32 accumulator rows (r = 4g .. 4g+3 of
+// the 32x32 C map, rows 8g + 4*(l>>5) + 0..3) as one packed 16-bit vector.
+template <int DT>
+__device__ __forceinline__ void store4(typename DTraits<DT>::T* dst, const floatx16& x,
+                                       int g, float mul) {
+  using P4 = typename Pack4<DT>::V;
+  P4 pk;
 #pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      k_frag[kc] = *(const frag*)(k + kvoff + (int64_t)kr_c * D + kc * 32 + hi * 8);
-      v_frag[kc] = *(const frag*)(v + voff + (int64_t)kr_c * v_rs + kc * 32 + hi * 8);
-    }
-  }
-
-  floatx4 dv_acc[NDN], dk_acc[NDN];
-#pragma unroll
-  for (int dn = 0; dn < NDN; ++dn) { dv_acc[dn] = (floatx4)(0.f); dk_acc[dn] = (floatx4)(0.f); }
-
-  const int qstart = (kt * 128) / QTT;       // first staged tile with these keys
-  const int nQT2 = (S + QTT - 1) / QTT;
-
-  // async staging state (QTT*D/8 = 512 loads: one piece per thread)
-  const int st_t = (int)threadIdx.x;
-  const bool st_on = st_t < (QTT * D) / 8;
-  const int st_row = st_t / (D / 8);
-  const int st_c8 = (st_t % (D / 8)) * 8;
-  frag qreg, dreg;
-  float lse_reg = 0.f, dl_reg = 0.f;
-
-  const int64_t gbase = (int64_t)b * g_sb + (int64_t)h * g_sh;
-  auto load_qtile = [&](int qt) {
-    const int qrow = qt * QTT + st_row;
-    const int qr_c = qrow < S ? qrow : S - 1;
-    if (st_on) {
-      qreg = *(const frag*)(q + qoff + (int64_t)qr_c * D + st_c8);
-      dreg = *(const frag*)(do_ + gbase + (int64_t)qr_c * g_sr + st_c8);
-    }
-    if (st_t < QTT) {
-      const int rr = qt * QTT + st_t;
-      const int rr_c = rr < S ? rr : S - 1;
-      lse_reg = lse[lseoff + rr_c];
-      dl_reg = delta[lseoff + rr_c];
-    }
-  };
-  auto write_qtile = [&](int buf) {
-    if (st_on) {
-      *(frag*)(Q_lds + buf * QTT * DS + st_row * DS + st_c8) = qreg;
-      *(frag*)(dO_lds + buf * QTT * DS + st_row * DS + st_c8) = dreg;
-    }
-    if (st_t < QTT) {
-      lse_lds[buf * QTT + st_t] = lse_reg;
-      dl_lds[buf * QTT + st_t] = dl_reg;
-    }
-  };
-
-  load_qtile(qstart);
-  write_qtile(0);
-  __syncthreads();
-
-  for (int qt = qstart; qt < nQT2; ++qt) {
-    const int cur = (qt - qstart) & 1;
-    T* Q64 = Q_lds + cur * QTT * DS;
-    T* dO64 = dO_lds + cur * QTT * DS;
-    const float* lse64 = lse_lds + cur * QTT;
-    const float* dl64 = dl_lds + cur * QTT;
-    if (qt + 1 < nQT2) load_qtile(qt + 1);
-
-    // two 32-q compute halves per staged 64-row tile: one barrier per 64 q
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-    const int qbase = qt * QTT + hf * QT;
-    T* Qb = Q64 + hf * QT * DS;
-    T* dOb = dO64 + hf * QT * DS;
-    const float* lse_b = lse64 + hf * QT;
-    const float* dl_b = dl64 + hf * QT;
-    // 8-wave WGs skew the diagonal: a wave whose 16 keys all sit above this
-    // q half (k0 > every qcol) computes an all-masked (zero) tile — skip.
-    if (qbase + QT > k0) {
-    // ---- S = Q K^T computed TRANSPOSED-C: mma(Q_as_A, K_as_B) ----
-    // The 16x16x32 A and B fragments share one lane map (row/col = l&15,
-    // k = 8*(l>>4)+j), so swapping the operands flips the C orientation
-    // for free: C row = q (hi*4+r), col = key (lo).  Each lane then holds
-    // 4 CONSECUTIVE q values for one key, which pack into the P^T/dS^T
-    // images ([16 key][QS] row-major, exactly the round-1 layout) as ONE
-    // ds_write_b64 instead of 16 scalar ds_write_b16 per image; the
-    // A-fragment reads stay the round-1 contiguous b128 reads, and the
-    // per-q lse/delta lookups become one float4 read per 16-q block.
-    float pt[2][4], dst[2][4];
-    __builtin_amdgcn_s_setprio(1);
-    const int krow = k0 + lo;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      floatx4 st = (floatx4)(0.f);
-      floatx4 dpt = (floatx4)(0.f);
-#pragma unroll
-      for (int kc = 0; kc < NKC; ++kc) {
-        frag qa = *(const frag*)(Qb + (nt * 16 + lo) * DS + kc * 32 + hi * 8);
-        st = MF::mma(qa, k_frag[kc], st);
-        frag doa = *(const frag*)(dOb + (nt * 16 + lo) * DS + kc * 32 + hi * 8);
-        dpt = MF::mma(doa, v_frag[kc], dpt);
-      }
-      const floatx4 lse4 = *(const floatx4*)(lse_b + nt * 16 + hi * 4);
-      const floatx4 dl4 = *(const floatx4*)(dl_b + nt * 16 + hi * 4);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int qrow = qbase + nt * 16 + hi * 4 + r;
-        float pv = 0.f;
-        if (krow <= qrow && krow < S && qrow < S)
-          pv = __expf(st[r] * scale - lse4[r]);
-        pt[nt][r] = pv;
-        dst[nt][r] = pv * (dpt[r] - dl4[r]) * scale;
-      }
-    }
-
-    // ---- dV += P^T dO  (A = P^T via packed per-wave LDS image; B = dO_T) ----
-    T* Pw = PT_lds + wave * 16 * QS;
-    using P4 = typename Pack4<DT>::V;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      P4 pk;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ((T*)&pk)[r] = TR::fromF(pt[nt][r]);
-      *(P4*)(Pw + lo * QS + nt * 16 + hi * 4) = pk;
-    }
-    frag pa = *(const frag*)(Pw + lo * QS + hi * 8);
-#pragma unroll
-    for (int dn = 0; dn < NDN; ++dn) {
-      frag bd = trread_bfrag<DT>(dOb, 0, dn * 16, DS, lane);
-      dv_acc[dn] = MF::mma(pa, bd, dv_acc[dn]);
-    }
-
-    // ---- dK += dS^T Q  (A = dS^T via the same packed image layout) ----
-    T* Dw = DS_lds + wave * 16 * QS;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      P4 dk4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ((T*)&dk4)[r] = TR::fromF(dst[nt][r]);
-      *(P4*)(Dw + lo * QS + nt * 16 + hi * 4) = dk4;
-    }
-    frag da = *(const frag*)(Dw + lo * QS + hi * 8);
-#pragma unroll
-    for (int dn = 0; dn < NDN; ++dn) {
-      frag bq = trread_bfrag<DT>(Qb, 0, dn * 16, DS, lane);
-      dk_acc[dn] = MF::mma(da, bq, dk_acc[dn]);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    }  // end diagonal skip
-    }  // end half loop
-
-    if (qt + 1 < nQT2) write_qtile(cur ^ 1);  // T14: write late
-    __syncthreads();
-  }
-
-  // ---- write dK, dV (per q-head layout [B,Hq,S,D]; caller sums GQA groups) ----
-  const int64_t dvoff = dv_sb ? ((int64_t)b * dv_sb + (int64_t)h * dv_sh) : qoff;
-  const int64_t dv_rs = dv_sb ? dv_sr : (int64_t)D;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int krow = k0 + hi * 4 + r;
-    if (krow >= S) continue;
-#pragma unroll
-    for (int dn = 0; dn < NDN; ++dn) {
-      dk_out[qoff + (int64_t)krow * D + dn * 16 + lo] = TR::fromF(dk_acc[dn][r]);
-      dv_out[dvoff + (int64_t)krow * dv_rs + dn * 16 + lo] = TR::fromF(dv_acc[dn][r]);
-    }
-  }
+  for (int i = 0; i < 4; ++i) ((typename DTraits<DT>::T*)&pk)[i] = DTraits<DT>::fromF(x[4 * g + i] * mul);
+  *(P4*)dst = pk;
 }
 
-// ======================= bwd dQ =======================
-// grid over (b, hq, q-tile of 128); 8 waves x 16 q rows each.  Loop kv
-// tiles of 64; dQ B-fragments tr_read from the row-major K image.
-// LDS: K[2][64][D+8] | V[2][64][D+8] | dS[8][16][64+8]
+// dQ: grid over (b, hq, q-tile of 128); 4 waves x 32 q rows.  Structurally
+// the v3 forward with K in place of V and dS in place of P:
+//   S^T = mfma(K, Q), dP^T = mfma(V, dO)   (q = lane&31, 16 keys per lane)
+//   dQ^T += K^T dS^T                        (A = K^T tr_read from row-major K)
+// LDS: K[2][64][D+8] | V[2][64][D+8], async double-buffered.
 template <int DT, int D>
-__global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
+__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(
     typename DTraits<DT>::T* __restrict__ dq_out,
     const typename DTraits<DT>::T* __restrict__ do_,
     const typename DTraits<DT>::T* __restrict__ q,
@@ -842,607 +658,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     int64_t v_sb, int64_t v_sh, int64_t v_sr) {
   using TR = DTraits<DT>;
   using T = typename TR::T;
-  using MF = MFMA16<DT>;
-  using frag = typename MF::frag;
-  constexpr int KT = 64;                      // kv tile (halves barrier count)
-  constexpr int KS = KT + 8;
-  constexpr int DS = D + 8;
-  constexpr int NKC = D / 32;
-  constexpr int NDN = D / 16;
-
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* K_lds = (T*)smem_raw;                    // [3][KT][DS] (triple ring)
-  T* V_lds = K_lds + 3 * KT * DS;             // [3][KT][DS]
-  T* S_lds = V_lds + 3 * KT * DS;             // [8][16][KS]  (dQ B-frags come
-                                              //  from row-major K via tr_read)
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int lo = lane & 15;
-  const int hi = lane >> 4;
-
-  const int nQT = (S + 127) / 128;            // 8 waves x 16 q rows per WG
-  int bid = blockIdx.x;
-  const int qt = bid % nQT;
-  const int h = (bid / nQT) % Hq;
-  const int b = bid / (nQT * Hq);
-  const int hkv = h / (Hq / Hkv);
-
-  const int q0 = qt * 128 + wave * 16;
-  const int64_t qoff = (((int64_t)b * Hq + h) * S) * D;
-  const int64_t kvoff = (((int64_t)b * Hkv + hkv) * S) * D;
-  const int64_t lseoff = ((int64_t)b * Hq + h) * S;
-  const int64_t voff = v_sb ? ((int64_t)b * v_sb + (int64_t)hkv * v_sh) : kvoff;
-  const int64_t v_rs = v_sb ? v_sr : (int64_t)D;
-
-  frag q_frag[NKC], do_frag[NKC];
-  float lse_q, dl_q;
-  const int qrow_l = q0 + lo;   // this lane's q row (C col after the operand swap)
-  {
-    const int qr_c = qrow_l < S ? qrow_l : S - 1;
-    const int64_t gbase = (int64_t)b * g_sb + (int64_t)h * g_sh;
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      q_frag[kc] = *(const frag*)(q + qoff + (int64_t)qr_c * D + kc * 32 + hi * 8);
-      do_frag[kc] = *(const frag*)(do_ + gbase + (int64_t)qr_c * g_sr + kc * 32 + hi * 8);
-    }
-    lse_q = lse[lseoff + qr_c];
-    dl_q = delta[lseoff + qr_c];
-  }
-
-  floatx4 dq_acc[NDN];
-#pragma unroll
-  for (int dn = 0; dn < NDN; ++dn) dq_acc[dn] = (floatx4)(0.f);
-
-  const int kv_end = min(S, qt * 128 + 128);
-  const int n_kt = (kv_end + KT - 1) / KT;
-
-  // async TRIPLE-buffered staging (prefetch distance 2: the t+2 load is
-  // issued at the START of tile t, the t+1 registers land in LDS at the
-  // END of tile t — ~2 compute tiles of load slack).  Two register sets
-  // (A = even tiles, B = odd) cost +8 VGPRs (120 total, still 4
-  // waves/SIMD); 3 LDS buffers fit 2 WGs/CU (147 KB).  MEASURED: a wash
-  // vs double-buffering (209 vs 212 TF) — dq's 50% parked
-  // (round2_attn_pmc.md) is LDS-read latency inside the mma loops and
-  // barrier convoy, not global staging slack.  Kept: equal speed,
-  // deeper slack for other shapes.
-  const int st_t = (int)threadIdx.x;
-  const bool st_on = st_t < (KT * D) / 8;
-  const int st_row = st_t / (D / 8);
-  const int st_c8 = (st_t % (D / 8)) * 8;
-  frag kregA, vregA, kregB, vregB;
-
-  auto load_ktile = [&](int kt, frag& kr, frag& vr) {
-    if (st_on) {
-      const int krow = kt * KT + st_row;
-      const int kr_c = krow < S ? krow : S - 1;
-      kr = *(const frag*)(k + kvoff + (int64_t)kr_c * D + st_c8);
-      vr = *(const frag*)(v + voff + (int64_t)kr_c * v_rs + st_c8);
-    }
-  };
-  auto write_ktile = [&](int buf, const frag& kr, const frag& vr) {
-    if (st_on) {
-      *(frag*)(K_lds + buf * KT * DS + st_row * DS + st_c8) = kr;
-      *(frag*)(V_lds + buf * KT * DS + st_row * DS + st_c8) = vr;
-    }
-  };
-
-  load_ktile(0, kregA, vregA);
-  write_ktile(0, kregA, vregA);
-  if (1 < n_kt) load_ktile(1, kregB, vregB);
-  __syncthreads();
-
-  for (int kt = 0; kt < n_kt; ++kt) {
-    const int kbase = kt * KT;
-    const int cur = kt % 3;
-    T* Kb = K_lds + cur * KT * DS;
-    T* Vb = V_lds + cur * KT * DS;
-    if (kt + 2 < n_kt) {
-      if ((kt + 2) & 1) load_ktile(kt + 2, kregB, vregB);
-      else load_ktile(kt + 2, kregA, vregA);
-    }
-
-    // wave-uniform diagonal skip (8-wave skew): if every key in this kv
-    // tile exceeds this wave's last q row, the whole tile is masked to zero.
-    if (kbase < q0 + 16) {
-    // S computed TRANSPOSED-C (see the dkdv kernel): mma(K_as_A, Q_as_B)
-    // puts C row = key (hi*4+r), col = q (lo), so each lane holds 4
-    // CONSECUTIVE keys of one q row — the dS^T image ([16 q][KS] row-major,
-    // round-1 layout) takes ONE packed ds_write_b64 per 16-key block
-    // instead of 16 scalar ds_write_b16, and the A-fragment reads stay the
-    // round-1 contiguous b128 reads.
-    float ds[4][4];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      floatx4 st = (floatx4)(0.f), dpt = (floatx4)(0.f);
-#pragma unroll
-      for (int kc = 0; kc < NKC; ++kc) {
-        frag ka = *(const frag*)(Kb + (nt * 16 + lo) * DS + kc * 32 + hi * 8);
-        st = MF::mma(ka, q_frag[kc], st);
-        frag va = *(const frag*)(Vb + (nt * 16 + lo) * DS + kc * 32 + hi * 8);
-        dpt = MF::mma(va, do_frag[kc], dpt);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int kcol = kbase + nt * 16 + hi * 4 + r;
-        float pv = 0.f;
-        if (kcol <= qrow_l && kcol < S && qrow_l < S)
-          pv = __expf(st[r] * scale - lse_q);
-        ds[nt][r] = pv * (dpt[r] - dl_q) * scale;
-      }
-    }
-
-    // dQ += dS K  (A = dS via the packed [16 q][KS] image; B from
-    // row-major K via tr_read); KT=64 keys = two 32-deep contraction chunks
-    T* Sw = S_lds + wave * 16 * KS;
-    using P4 = typename Pack4<DT>::V;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      P4 s4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ((T*)&s4)[r] = TR::fromF(ds[nt][r]);
-      *(P4*)(Sw + lo * KS + nt * 16 + hi * 4) = s4;
-    }
-    frag da[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) da[c] = *(const frag*)(Sw + lo * KS + c * 32 + hi * 8);
-#pragma unroll
-    for (int dn = 0; dn < NDN; ++dn)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        frag bk = trread_bfrag<DT>(Kb, c * 32, dn * 16, DS, lane);
-        dq_acc[dn] = MF::mma(da[c], bk, dq_acc[dn]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-    }  // end diagonal skip
-
-    if (kt + 1 < n_kt) {  // T14: write late (registers loaded last iteration)
-      if ((kt + 1) & 1) write_ktile((kt + 1) % 3, kregB, vregB);
-      else write_ktile((kt + 1) % 3, kregA, vregA);
-    }
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int qrow = q0 + hi * 4 + r;
-    if (qrow >= S) continue;
-#pragma unroll
-    for (int dn = 0; dn < NDN; ++dn)
-      dq_out[qoff + (int64_t)qrow * D + dn * 16 + lo] = TR::fromF(dq_acc[dn][r]);
-  }
-}
-
-// ======================= bwd v3: 32x32 MFMA tiles =======================
-// Same split (dK/dV over kv tiles, dQ over q tiles) and the same staged
-// images as v2, but on mfma_f32_32x32x16 tiles: a wave owns 32 keys (dkdv)
-// or 32 q rows (dq) and the workgroup covers 128, halving the MFMA / LDS
-// fragment-read instruction count per FLOP.  P^T / dS^T still re-shape
-// C->A through per-wave LDS tiles (a half-lane swap cannot transpose them).
-
-template <int DT, int D>
-__global__ __launch_bounds__(256) void attn_bwd_dkdv_v3_kernel(
-    typename DTraits<DT>::T* __restrict__ dk_out,
-    typename DTraits<DT>::T* __restrict__ dv_out,
-    const typename DTraits<DT>::T* __restrict__ do_,
-    const typename DTraits<DT>::T* __restrict__ q,
-    const typename DTraits<DT>::T* __restrict__ k,
-    const typename DTraits<DT>::T* __restrict__ v,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    int B, int Hq, int Hkv, int S, float scale,
-    int64_t g_sb, int64_t g_sh, int64_t g_sr) {
-  using TR = DTraits<DT>;
-  using T = typename TR::T;
   using MF = MFMA32<DT>;
   using frag = typename MF::frag;
-  constexpr int QT = 32;
-  constexpr int QS = QT + 8;
+  constexpr int KT = 64;            // staged kv tile (2 x 32-key subtiles)
   constexpr int DS = D + 8;
-  constexpr int NKC = D / 16;
-  constexpr int NMT = D / 32;
+  constexpr int NKC = D / 16;       // 16-deep contraction chunks for S^T, dP^T
+  constexpr int NMT = D / 32;       // 32-row d tiles of dQ^T
+  constexpr int LPT = (KT * D) / 8 / 256;
 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Q_lds = (T*)smem_raw;                   // [2][QT][DS]
-  T* dO_lds = Q_lds + 2 * QT * DS;           // [2][QT][DS]
-  T* PT_lds = dO_lds + 2 * QT * DS;          // [4][32][QS]
-  T* DST_lds = PT_lds + 4 * 32 * QS;         // [4][32][QS]
-  float* lse_lds = (float*)(DST_lds + 4 * 32 * QS);  // [2][QT]
-  float* dl_lds = lse_lds + 2 * QT;                  // [2][QT]
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int lo32 = lane & 31;
-  const int hi5 = lane >> 5;
-
-  const int nKT = (S + 127) / 128;
-  int bid = blockIdx.x;
-  const int kt = bid % nKT;
-  const int h = (bid / nKT) % Hq;
-  const int b = bid / (nKT * Hq);
-  const int hkv = h / (Hq / Hkv);
-
-  const int k0 = kt * 128 + wave * 32;       // wave's first key
-  const int64_t qoff = (((int64_t)b * Hq + h) * S) * D;
-  const int64_t kvoff = (((int64_t)b * Hkv + hkv) * S) * D;
-  const int64_t lseoff = ((int64_t)b * Hq + h) * S;
-
-  // K,V A-fragment base (A row = key = lane&31); fragments are re-read per
-  // q-tile from L2 instead of held in registers — frees 32 VGPRs so the
-  // kernel fits 3 waves/SIMD without spills
-  const int kr_c0 = (k0 + lo32) < S ? (k0 + lo32) : S - 1;
-  const T* kbase_p = k + kvoff + (int64_t)kr_c0 * D + hi5 * 8;
-  const T* vbase_p = v + kvoff + (int64_t)kr_c0 * D + hi5 * 8;
-
-  floatx16 dv_acc[NMT], dk_acc[NMT];
-#pragma unroll
-  for (int mt = 0; mt < NMT; ++mt) { dv_acc[mt] = (floatx16)(0.f); dk_acc[mt] = (floatx16)(0.f); }
-
-  const int qstart = (kt * 128) / QT;
-  const int nQT2 = (S + QT - 1) / QT;
-
-  const int st_t = (int)threadIdx.x;
-  const bool st_on = st_t < (QT * D) / 8;
-  const int st_row = st_t / (D / 8);
-  const int st_c8 = (st_t % (D / 8)) * 8;
-  shortx8 qreg, dreg;
-  float lse_reg = 0.f, dl_reg = 0.f;
-  const int64_t gbase = (int64_t)b * g_sb + (int64_t)h * g_sh;
-
-  auto load_qtile = [&](int qt2) {
-    const int qrow = qt2 * QT + st_row;
-    const int qr_c = qrow < S ? qrow : S - 1;
-    if (st_on) {
-      qreg = *(const shortx8*)(q + qoff + (int64_t)qr_c * D + st_c8);
-      dreg = *(const shortx8*)(do_ + gbase + (int64_t)qr_c * g_sr + st_c8);
-    }
-    if (st_t < QT) {
-      const int rr = qt2 * QT + st_t;
-      const int rr_c = rr < S ? rr : S - 1;
-      lse_reg = lse[lseoff + rr_c];
-      dl_reg = delta[lseoff + rr_c];
-    }
-  };
-  auto write_qtile = [&](int buf) {
-    if (st_on) {
-      *(shortx8*)(Q_lds + buf * QT * DS + st_row * DS + st_c8) = qreg;
-      *(shortx8*)(dO_lds + buf * QT * DS + st_row * DS + st_c8) = dreg;
-    }
-    if (st_t < QT) {
-      lse_lds[buf * QT + st_t] = lse_reg;
-      dl_lds[buf * QT + st_t] = dl_reg;
-    }
-  };
-
-  load_qtile(qstart);
-  write_qtile(0);
-  __syncthreads();
-
-  for (int qt2 = qstart; qt2 < nQT2; ++qt2) {
-    const int qbase = qt2 * QT;
-    const int cur = (qt2 - qstart) & 1;
-    T* Qb = Q_lds + cur * QT * DS;
-    T* dOb = dO_lds + cur * QT * DS;
-    const float* lse_b = lse_lds + cur * QT;
-    const float* dl_b = dl_lds + cur * QT;
-    if (qt2 + 1 < nQT2) load_qtile(qt2 + 1);
-
-    // ---- S^T = K Q^T and dP^T = V dO^T  (C: col = q = lane&31) ----
-    floatx16 st = (floatx16)(0.f), dpt = (floatx16)(0.f);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      frag ka = *(const frag*)(kbase_p + kc * 16);
-      frag bq = *(const frag*)(Qb + lo32 * DS + kc * 16 + hi5 * 8);
-      st = MF::mma(ka, bq, st);
-      frag va = *(const frag*)(vbase_p + kc * 16);
-      frag bd = *(const frag*)(dOb + lo32 * DS + kc * 16 + hi5 * 8);
-      dpt = MF::mma(va, bd, dpt);
-    }
-    __builtin_amdgcn_s_setprio(0);
-
-    const int qcol = qbase + lo32;
-    const float lse_q = lse_b[lo32];
-    const float dl_q = dl_b[lo32];
-    const bool full = (qbase >= k0 + 32) && (qbase + QT <= S);
-    float pt[16], dst[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float pv;
-      if (full) {
-        pv = __expf(st[r] * scale - lse_q);
-      } else {
-        const int krow = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-        pv = 0.f;
-        if (krow <= qcol && krow < S && qcol < S)
-          pv = __expf(st[r] * scale - lse_q);
-      }
-      pt[r] = pv;
-      dst[r] = pv * (dpt[r] - dl_q) * scale;
-    }
-
-    // ---- dV += P^T dO (A = P^T via LDS; B = dO_T) ----
-    T* Pw = PT_lds + wave * 32 * QS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      Pw[((r & 3) + 8 * (r >> 2) + 4 * hi5) * QS + lo32] = TR::fromF(pt[r]);
-    frag pa[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-      pa[c] = *(const frag*)(Pw + lo32 * QS + c * 16 + hi5 * 8);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        frag bd = trread_afrag32<DT>(dOb, c * 16, mt * 32, DS, lane);
-        dv_acc[mt] = MF::mma(pa[c], bd, dv_acc[mt]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-
-    // ---- dK += dS^T Q (A = dS^T via LDS; B = Q_T) ----
-    T* Dw = DST_lds + wave * 32 * QS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      Dw[((r & 3) + 8 * (r >> 2) + 4 * hi5) * QS + lo32] = TR::fromF(dst[r]);
-    frag da[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-      da[c] = *(const frag*)(Dw + lo32 * QS + c * 16 + hi5 * 8);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        frag bq = trread_afrag32<DT>(Qb, c * 16, mt * 32, DS, lane);
-        dk_acc[mt] = MF::mma(da[c], bq, dk_acc[mt]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-
-    if (qt2 + 1 < nQT2) write_qtile(cur ^ 1);
-    __syncthreads();
-  }
-
-  // ---- write dK, dV (per q-head layout; caller sums GQA groups) ----
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int krow = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-    if (krow >= S) continue;
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt) {
-      dk_out[qoff + (int64_t)krow * D + mt * 32 + lo32] = TR::fromF(dk_acc[mt][r]);
-      dv_out[qoff + (int64_t)krow * D + mt * 32 + lo32] = TR::fromF(dv_acc[mt][r]);
-    }
-  }
-}
-
-// ======================= bwd split-32: dv-only / dk-only =======================
-// The fused kernels carry BOTH accumulator sets (dV and dK) and are
-// VGPR-capped at 4 (16x16) / 2 (32x32) waves per SIMD while the matrix
-// pipe idles at ~11% (profiles/round2_attn_pmc.md) — issue/latency bound.
-// Splitting halves the accumulators: each kernel holds ONE floatx16[D/32]
-// set on 32x32x16 tiles (2x the FLOP per instruction of the 16x16 path),
-// recomputes S from lse, and occupies 4-5 waves/SIMD.  QK^T is recomputed
-// by both kernels (+25% matrix-pipe work) against a ~40% cut in issue
-// slots per FLOP.  The mma runs OPERAND-SWAPPED (A/B lane maps coincide)
-// so each lane's C holds 4 consecutive q per key: the P^T / dS^T staging
-// image takes 4 packed ds_write_b64 instead of 16 scalar ds_write_b16 and
-// the lse/delta lookups are float4 reads (same trick as the 16x16 pair).
-// Grid over (b, hq, kv-tile of 128); 4 waves x 32 keys; q-tiles of 32,
-// double-buffered.  Strided dO/V/dV supported (runs in-model, unlike the
-// contiguous-only fused 32x32 port).  WANT_DK=0: dV += P^T dO.
-// WANT_DK=1: dK += dS^T Q with dS^T = P^T o (dP^T - delta) * scale.
-template <int DT, int D, int WANT_DK>
-__global__ __launch_bounds__(256) void attn_bwd_split32_kernel(
-    typename DTraits<DT>::T* __restrict__ out,      // dV or dK
-    const typename DTraits<DT>::T* __restrict__ do_,
-    const typename DTraits<DT>::T* __restrict__ q,
-    const typename DTraits<DT>::T* __restrict__ k,
-    const typename DTraits<DT>::T* __restrict__ v,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    int B, int Hq, int Hkv, int S, float scale,
-    int64_t g_sb, int64_t g_sh, int64_t g_sr,
-    int64_t v_sb, int64_t v_sh, int64_t v_sr,
-    int64_t o_sb, int64_t o_sh, int64_t o_sr) {   // out strides (0 = BHSD)
-  using TR = DTraits<DT>;
-  using T = typename TR::T;
-  using MF = MFMA32<DT>;
-  using frag = typename MF::frag;
-  using P4 = typename Pack4<DT>::V;
-  constexpr int QT = 32;
-  constexpr int QS = QT + 8;
-  constexpr int DS = D + 8;
-  constexpr int NKC = D / 16;
-  constexpr int NMT = D / 32;
-
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* Q_lds = (T*)smem_raw;                   // [2][QT][DS]
-  T* dO_lds = Q_lds + 2 * QT * DS;           // [2][QT][DS]
-  T* PT_lds = dO_lds + 2 * QT * DS;          // [4][32][QS] (P^T or dS^T)
-  float* lse_lds = (float*)(PT_lds + 4 * 32 * QS);   // [2][QT]
-  float* dl_lds = lse_lds + 2 * QT;                  // [2][QT] (dk only)
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int lo32 = lane & 31;
-  const int hi5 = lane >> 5;
-
-  const int nKT = (S + 127) / 128;
-  int bid = blockIdx.x;
-  const int kt = bid % nKT;
-  const int h = (bid / nKT) % Hq;
-  const int b = bid / (nKT * Hq);
-  const int hkv = h / (Hq / Hkv);
-
-  const int k0 = kt * 128 + wave * 32;
-  const int64_t qoff = (((int64_t)b * Hq + h) * S) * D;
-  const int64_t kvoff = (((int64_t)b * Hkv + hkv) * S) * D;
-  const int64_t lseoff = ((int64_t)b * Hq + h) * S;
-  const int64_t voff = v_sb ? ((int64_t)b * v_sb + (int64_t)hkv * v_sh) : kvoff;
-  const int64_t v_rs = v_sb ? v_sr : (int64_t)D;
-
-  // K (and V for dk) B-fragment base: re-read from L2 per q-tile, freeing
-  // the register copies (v3-port trick)
-  const int kr_c0 = (k0 + lo32) < S ? (k0 + lo32) : S - 1;
-  const T* kbase_p = k + kvoff + (int64_t)kr_c0 * D + hi5 * 8;
-  const T* vbase_p = v + voff + (int64_t)kr_c0 * v_rs + hi5 * 8;
-
-  floatx16 acc[NMT];
-#pragma unroll
-  for (int mt = 0; mt < NMT; ++mt) acc[mt] = (floatx16)(0.f);
-
-  const int qstart = (kt * 128) / QT;
-  const int nQT2 = (S + QT - 1) / QT;
-
-  const int st_t = (int)threadIdx.x;
-  const bool st_on = st_t < (QT * D) / 8;
-  const int st_row = st_t / (D / 8);
-  const int st_c8 = (st_t % (D / 8)) * 8;
-  shortx8 qreg, dreg;
-  float lse_reg = 0.f, dl_reg = 0.f;
-  const int64_t gbase = (int64_t)b * g_sb + (int64_t)h * g_sh;
-
-  auto load_qtile = [&](int qt2) {
-    const int qrow = qt2 * QT + st_row;
-    const int qr_c = qrow < S ? qrow : S - 1;
-    if (st_on) {
-      qreg = *(const shortx8*)(q + qoff + (int64_t)qr_c * D + st_c8);
-      dreg = *(const shortx8*)(do_ + gbase + (int64_t)qr_c * g_sr + st_c8);
-    }
-    if (st_t < QT) {
-      const int rr = qt2 * QT + st_t;
-      const int rr_c = rr < S ? rr : S - 1;
-      lse_reg = lse[lseoff + rr_c];
-      if (WANT_DK) dl_reg = delta[lseoff + rr_c];
-    }
-  };
-  auto write_qtile = [&](int buf) {
-    if (st_on) {
-      *(shortx8*)(Q_lds + buf * QT * DS + st_row * DS + st_c8) = qreg;
-      *(shortx8*)(dO_lds + buf * QT * DS + st_row * DS + st_c8) = dreg;
-    }
-    if (st_t < QT) {
-      lse_lds[buf * QT + st_t] = lse_reg;
-      if (WANT_DK) dl_lds[buf * QT + st_t] = dl_reg;
-    }
-  };
-
-  load_qtile(qstart);
-  write_qtile(0);
-  __syncthreads();
-
-  for (int qt2 = qstart; qt2 < nQT2; ++qt2) {
-    const int qbase = qt2 * QT;
-    const int cur = (qt2 - qstart) & 1;
-    T* Qb = Q_lds + cur * QT * DS;
-    T* dOb = dO_lds + cur * QT * DS;
-    const float* lse_b = lse_lds + cur * QT;
-    const float* dl_b = dl_lds + cur * QT;
-    if (qt2 + 1 < nQT2) load_qtile(qt2 + 1);
-
-    // ---- S (and dP for dk) TRANSPOSED-C: C col = key = lo32,
-    //      row = q = (r&3) + 8*(r>>2) + 4*hi5 ----
-    floatx16 st = (floatx16)(0.f), dpt = (floatx16)(0.f);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      frag qa = *(const frag*)(Qb + lo32 * DS + kc * 16 + hi5 * 8);
-      frag kb = *(const frag*)(kbase_p + kc * 16);
-      st = MF::mma(qa, kb, st);
-      if (WANT_DK) {
-        frag doa = *(const frag*)(dOb + lo32 * DS + kc * 16 + hi5 * 8);
-        frag vb = *(const frag*)(vbase_p + kc * 16);
-        dpt = MF::mma(doa, vb, dpt);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-
-    const int krow = k0 + lo32;
-    const bool full = (qbase >= k0 + 32) && (qbase + QT <= S);
-    // pack P^T (dv) or dS^T (dk) into the [32 key][QS] row-major image,
-    // one ds_write_b64 per 4 consecutive q
-    T* Pw = PT_lds + wave * 32 * QS;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int qloc = 8 * g + 4 * hi5;
-      const floatx4 lse4 = *(const floatx4*)(lse_b + qloc);
-      floatx4 dl4;
-      if (WANT_DK) dl4 = *(const floatx4*)(dl_b + qloc);
-      P4 pk;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = g * 4 + r;
-        float pv;
-        if (full) {
-          pv = __expf(st[i] * scale - lse4[r]);
-        } else {
-          const int qrow = qbase + qloc + r;
-          pv = 0.f;
-          if (krow <= qrow && krow < S && qrow < S)
-            pv = __expf(st[i] * scale - lse4[r]);
-        }
-        if (WANT_DK) pv = pv * (dpt[i] - dl4[r]) * scale;
-        ((T*)&pk)[r] = TR::fromF(pv);
-      }
-      *(P4*)(Pw + lo32 * QS + qloc) = pk;
-    }
-
-    // ---- acc += A(P^T|dS^T) x B(dO_T|Q_T) ----
-    frag pa[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-      pa[c] = *(const frag*)(Pw + lo32 * QS + c * 16 + hi5 * 8);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        frag bb = trread_afrag32<DT>(WANT_DK ? Qb : dOb, c * 16, mt * 32, DS, lane);
-        acc[mt] = MF::mma(pa[c], bb, acc[mt]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-
-    if (qt2 + 1 < nQT2) write_qtile(cur ^ 1);
-    __syncthreads();
-  }
-
-  // ---- write dV / dK (per q-head; caller sums GQA groups) ----
-  const int64_t obase = o_sb ? ((int64_t)b * o_sb + (int64_t)h * o_sh) : qoff;
-  const int64_t o_rs = o_sb ? o_sr : (int64_t)D;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int kr = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-    if (kr >= S) continue;
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt)
-      out[obase + (int64_t)kr * o_rs + mt * 32 + lo32] = TR::fromF(acc[mt][r]);
-  }
-}
-
-template <int DT, int D>
-__global__ __launch_bounds__(256) void attn_bwd_dq_v3_kernel(
-    typename DTraits<DT>::T* __restrict__ dq_out,
-    const typename DTraits<DT>::T* __restrict__ do_,
-    const typename DTraits<DT>::T* __restrict__ q,
-    const typename DTraits<DT>::T* __restrict__ k,
-    const typename DTraits<DT>::T* __restrict__ v,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    int B, int Hq, int Hkv, int S, float scale,
-    int64_t g_sb, int64_t g_sh, int64_t g_sr) {
-  using TR = DTraits<DT>;
-  using T = typename TR::T;
-  using MF = MFMA32<DT>;
-  using frag = typename MF::frag;
-  constexpr int KT = 32;
-  constexpr int KS = KT + 8;
-  constexpr int DS = D + 8;
-  constexpr int NKC = D / 16;
-  constexpr int NMT = D / 32;
-
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* K_lds = (T*)smem_raw;                    // [2][KT][DS]
-  T* V_lds = K_lds + 2 * KT * DS;             // [2][KT][DS]
-  T* S_lds = V_lds + 2 * KT * DS;             // [4][32][KS]
+  T* K_lds = (T*)smem_raw;                       // [2][KT][DS]
+  T* V_lds = K_lds + 2 * KT * DS;                // [2][KT][DS]
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1457,30 +683,28 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_v3_kernel(
   const int hkv = h / (Hq / Hkv);
 
   const int q0 = qt * 128 + wave * 32;
+  const int qrow = q0 + lo32;
   const int64_t qoff = (((int64_t)b * Hq + h) * S) * D;
   const int64_t kvoff = (((int64_t)b * Hkv + hkv) * S) * D;
   const int64_t lseoff = ((int64_t)b * Hq + h) * S;
+  const int64_t voff = v_sb ? ((int64_t)b * v_sb + (int64_t)hkv * v_sh) : kvoff;
+  const int64_t v_rs = v_sb ? v_sr : (int64_t)D;
+  const int64_t gbase = (int64_t)b * g_sb + (int64_t)h * g_sh;
 
-  // A-fragments (row = q = lane&31) + per-C-row lse/delta
+  // Q / dO B-fragments: slot j of chunk kc = X[qrow][kc*16 + hi5*8 + j]
   frag q_frag[NKC], do_frag[NKC];
-  float lse_r[16], dl_r[16];
+  float nl2, dl_q;   // -lse*log2(e), delta of this lane's row
   {
-    const int qrow = q0 + lo32;
     const int qr_c = qrow < S ? qrow : S - 1;
-    const int64_t gb = (int64_t)b * g_sb + (int64_t)h * g_sh;
 #pragma unroll
     for (int kc = 0; kc < NKC; ++kc) {
       q_frag[kc] = *(const frag*)(q + qoff + (int64_t)qr_c * D + kc * 16 + hi5 * 8);
-      do_frag[kc] = *(const frag*)(do_ + gb + (int64_t)qr_c * g_sr + kc * 16 + hi5 * 8);
+      do_frag[kc] = *(const frag*)(do_ + gbase + (int64_t)qr_c * g_sr + kc * 16 + hi5 * 8);
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rr = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-      const int rr_c = rr < S ? rr : S - 1;
-      lse_r[r] = lse[lseoff + rr_c];
-      dl_r[r] = delta[lseoff + rr_c];
-    }
+    nl2 = -lse[lseoff + qr_c] * 1.4426950408889634f;
+    dl_q = delta[lseoff + qr_c];
   }
+  const float c2 = scale * 1.4426950408889634f;  // scale * log2(e)
 
   floatx16 dq_acc[NMT];
 #pragma unroll
@@ -1489,97 +713,308 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_v3_kernel(
   const int kv_end = min(S, qt * 128 + 128);
   const int n_kt = (kv_end + KT - 1) / KT;
 
-  const int st_t = (int)threadIdx.x;
-  const bool st_on = st_t < (KT * D) / 8;
-  const int st_row = st_t / (D / 8);
-  const int st_c8 = (st_t % (D / 8)) * 8;
-  shortx8 kreg, vreg;
-
-  auto load_ktile = [&](int kt2) {
-    if (st_on) {
-      const int krow = kt2 * KT + st_row;
+  shortx8 kreg[LPT], vreg[LPT];
+  int st_row[LPT], st_c8[LPT];
+#pragma unroll
+  for (int i = 0; i < LPT; ++i) {
+    st_row[i] = (int)(threadIdx.x + 256 * i) / (D / 8);
+    st_c8[i] = ((int)(threadIdx.x + 256 * i) % (D / 8)) * 8;
+  }
+  auto load_tile = [&](int kt) {
+#pragma unroll
+    for (int i = 0; i < LPT; ++i) {
+      const int krow = kt * KT + st_row[i];
       const int kr_c = krow < S ? krow : S - 1;
-      kreg = *(const shortx8*)(k + kvoff + (int64_t)kr_c * D + st_c8);
-      vreg = *(const shortx8*)(v + kvoff + (int64_t)kr_c * D + st_c8);
+      kreg[i] = *(const shortx8*)(k + kvoff + (int64_t)kr_c * D + st_c8[i]);
+      vreg[i] = *(const shortx8*)(v + voff + (int64_t)kr_c * v_rs + st_c8[i]);
     }
   };
-  auto write_ktile = [&](int buf) {
-    if (st_on) {
-      *(shortx8*)(K_lds + buf * KT * DS + st_row * DS + st_c8) = kreg;
-      *(shortx8*)(V_lds + buf * KT * DS + st_row * DS + st_c8) = vreg;
+  auto write_tile = [&](int buf) {
+    T* Kb = K_lds + buf * KT * DS;
+    T* Vb = V_lds + buf * KT * DS;
+#pragma unroll
+    for (int i = 0; i < LPT; ++i) {
+      *(shortx8*)(Kb + st_row[i] * DS + st_c8[i]) = kreg[i];
+      *(shortx8*)(Vb + st_row[i] * DS + st_c8[i]) = vreg[i];
     }
   };
 
-  load_ktile(0);
-  write_ktile(0);
+  load_tile(0);
+  write_tile(0);
   __syncthreads();
 
-  for (int kt2 = 0; kt2 < n_kt; ++kt2) {
-    const int kbase = kt2 * KT;
-    const int cur = kt2 & 1;
-    T* Kb = K_lds + cur * KT * DS;
-    T* Vb = V_lds + cur * KT * DS;
-    if (kt2 + 1 < n_kt) load_ktile(kt2 + 1);
+  for (int kt = 0; kt < n_kt; ++kt) {
+    const int cur = kt & 1;
+    const T* Kb = K_lds + cur * KT * DS;
+    const T* Vb = V_lds + cur * KT * DS;
+    if (kt + 1 < n_kt) load_tile(kt + 1);
 
-    // ---- S = Q K^T and dP = dO V^T  (C: col = key = lane&31) ----
-    floatx16 st = (floatx16)(0.f), dpt = (floatx16)(0.f);
-    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      frag bk = *(const frag*)(Kb + lo32 * DS + kc * 16 + hi5 * 8);
-      st = MF::mma(q_frag[kc], bk, st);
-      frag bv = *(const frag*)(Vb + lo32 * DS + kc * 16 + hi5 * 8);
-      dpt = MF::mma(do_frag[kc], bv, dpt);
-    }
-    __builtin_amdgcn_s_setprio(0);
-
-    const int kcol = kbase + lo32;
-    const bool full = (kbase + KT <= q0) && (kbase + KT <= S) && (q0 + 32 <= S);
-    float ds[16];
+    for (int st = 0; st < 2; ++st) {
+      const int sbase = kt * KT + st * 32;
+      if (sbase >= q0 + 32) continue;            // wave-uniform: fully masked
+      floatx16 sc = (floatx16)(0.f), dp = (floatx16)(0.f);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float pv;
-      if (full) {
-        pv = __expf(st[r] * scale - lse_r[r]);
-      } else {
-        const int qrow = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-        pv = 0.f;
-        if (kcol <= qrow && kcol < S && qrow < S)
-          pv = __expf(st[r] * scale - lse_r[r]);
+      for (int kc = 0; kc < NKC; ++kc) {
+        frag ka = *(const frag*)(Kb + (st * 32 + lo32) * DS + kc * 16 + hi5 * 8);
+        sc = MF::mma(ka, q_frag[kc], sc);
+        frag va = *(const frag*)(Vb + (st * 32 + lo32) * DS + kc * 16 + hi5 * 8);
+        dp = MF::mma(va, do_frag[kc], dp);
       }
-      ds[r] = pv * (dpt[r] - dl_r[r]) * scale;
+      __builtin_amdgcn_s_setprio(0);
+
+      // dS^T in dp.  Off the diagonal every key (< sbase + 32 <= q0) is
+      // below every q row of the wave, and for a valid row (< S) every such
+      // key is valid too: no compares.  Rows >= S only feed their own
+      // (unstored) dQ^T column.
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = (dp[r] - dl_q) * exp2_fast(fmaf(sc[r], c2, nl2));
+      if (sbase >= q0) {                       // diagonal subtile only
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = sbase + (r & 3) + 8 * (r >> 2) + 4 * hi5;
+          if (key > qrow) dp[r] = 0.f;
+        }
+      }
+      frag dsf[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) dsf[c] = pack_frag32<DT>(dp, c);
+
+      // ---- dQ^T += K^T dS^T  (A = K^T tr_read from the row-major K image) ----
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          frag ka = trread_afrag32<DT>(Kb, st * 32 + c * 16, mt * 32, DS, lane);
+          dq_acc[mt] = MF::mma(ka, dsf[c], dq_acc[mt]);
+        }
+      __builtin_amdgcn_s_setprio(0);
     }
 
-    // ---- dQ += dS K (A = dS via LDS; B = K_T) ----
-    T* Sw = S_lds + wave * 32 * KS;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      Sw[((r & 3) + 8 * (r >> 2) + 4 * hi5) * KS + lo32] = TR::fromF(ds[r]);
-    frag da[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-      da[c] = *(const frag*)(Sw + lo32 * KS + c * 16 + hi5 * 8);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        frag bk = trread_afrag32<DT>(Kb, c * 16, mt * 32, DS, lane);
-        dq_acc[mt] = MF::mma(da[c], bk, dq_acc[mt]);
-      }
-    __builtin_amdgcn_s_setprio(0);
-
-    if (kt2 + 1 < n_kt) write_ktile(cur ^ 1);
+    if (kt + 1 < n_kt) write_tile((kt + 1) & 1);
     __syncthreads();
   }
 
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int qrow = q0 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-    if (qrow >= S) continue;
+  // lane q = lo32 owns its row of dQ^T: d = mt*32 + 8g + 4*hi5 + 0..3
+  if (qrow < S) {
+    T* dst = dq_out + qoff + (int64_t)qrow * D;
 #pragma unroll
     for (int mt = 0; mt < NMT; ++mt)
-      dq_out[qoff + (int64_t)qrow * D + mt * 32 + lo32] = TR::fromF(dq_acc[mt][r]);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) store4<DT>(dst + mt * 32 + 8 * g + 4 * hi5, dq_acc[mt], g, scale);
+  }
+}
+
+// dK/dV: grid over (b, hq, kv-tile of 128 keys); 4 waves x 32 keys.  The
+// workgroup sweeps q tiles of 64 (two 32-row compute halves per barrier):
+//   S = mfma(Q, K), dP = mfma(dO, V)       (key = lane&31, 16 q rows per lane)
+//   dV^T += dO^T P,  dK^T += Q^T dS         (A = dO^T / Q^T tr_read from the
+//                                            row-major staged images)
+// K/V B-fragments stay in registers for the whole sweep.  The per-row
+// constants (-lse/scale, -delta) are staged next to Q/dO and loaded straight
+// into the S / dP accumulators (4 x ds_read_b128 each per half).
+// LDS: Q[2][64][D+8] | dO[2][64][D+8] | lse'[2][64] f32 | -delta[2][64] f32
+template <int DT, int D>
+__global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(
+    typename DTraits<DT>::T* __restrict__ dk_out,
+    typename DTraits<DT>::T* __restrict__ dv_out,
+    const typename DTraits<DT>::T* __restrict__ do_,
+    const typename DTraits<DT>::T* __restrict__ q,
+    const typename DTraits<DT>::T* __restrict__ k,
+    const typename DTraits<DT>::T* __restrict__ v,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    int B, int Hq, int Hkv, int S, float scale,
+    int64_t g_sb, int64_t g_sh, int64_t g_sr,
+    int64_t v_sb, int64_t v_sh, int64_t v_sr,
+    int64_t dv_sb, int64_t dv_sh, int64_t dv_sr) {
+  using TR = DTraits<DT>;
+  using T = typename TR::T;
+  using MF = MFMA32<DT>;
+  using frag = typename MF::frag;
+  constexpr int QT = 32;                     // compute half (q rows)
+  constexpr int QTT = 32;                    // staged tile (one per barrier)
+  constexpr int DS = D + 8;
+  constexpr int NKC = D / 16;
+  constexpr int NMT = D / 32;
+  constexpr int NCH = (QTT * D) / 8;         // 16-byte staging pieces per tensor
+  constexpr int LPT = (NCH + 255) / 256;
+
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* Q_lds = (T*)smem_raw;                   // [2][QTT][DS]
+  T* dO_lds = Q_lds + 2 * QTT * DS;          // [2][QTT][DS]
+  float* lse_lds = (float*)(dO_lds + 2 * QTT * DS);  // [2][QTT]  -lse/scale
+  float* dl_lds = lse_lds + 2 * QTT;                 // [2][QTT]  -delta
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int lo32 = lane & 31;
+  const int hi5 = lane >> 5;
+
+  const int nKT = (S + 127) / 128;
+  int bid = blockIdx.x;
+  const int kt = bid % nKT;
+  const int h = (bid / nKT) % Hq;
+  const int b = bid / (nKT * Hq);
+  const int hkv = h / (Hq / Hkv);
+
+  const int k0 = kt * 128 + wave * 32;       // this wave's first key
+  const int key = k0 + lo32;                 // this lane's key
+  const int64_t qoff = (((int64_t)b * Hq + h) * S) * D;
+  const int64_t kvoff = (((int64_t)b * Hkv + hkv) * S) * D;
+  const int64_t lseoff = ((int64_t)b * Hq + h) * S;
+  const int64_t voff = v_sb ? ((int64_t)b * v_sb + (int64_t)hkv * v_sh) : kvoff;
+  const int64_t v_rs = v_sb ? v_sr : (int64_t)D;
+  const int64_t gbase = (int64_t)b * g_sb + (int64_t)h * g_sh;
+
+  // K / V B-fragments: slot j of chunk kc = X[key][kc*16 + hi5*8 + j]
+  frag k_frag[NKC], v_frag[NKC];
+  {
+    const int kr_c = key < S ? key : S - 1;
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) {
+      k_frag[kc] = *(const frag*)(k + kvoff + (int64_t)kr_c * D + kc * 16 + hi5 * 8);
+      v_frag[kc] = *(const frag*)(v + voff + (int64_t)kr_c * v_rs + kc * 16 + hi5 * 8);
+    }
+  }
+  const float c2 = scale * 1.4426950408889634f;
+
+  floatx16 dv_acc[NMT], dk_acc[NMT];
+#pragma unroll
+  for (int mt = 0; mt < NMT; ++mt) { dv_acc[mt] = (floatx16)(0.f); dk_acc[mt] = (floatx16)(0.f); }
+
+  const int qstart = (kt * 128) / QTT;
+  const int nQT2 = (S + QTT - 1) / QTT;
+
+  shortx8 qreg[LPT], dreg[LPT];
+  float lse_reg = 0.f, dl_reg = 0.f;
+  int st_row[LPT], st_c8[LPT];
+#pragma unroll
+  for (int i = 0; i < LPT; ++i) {
+    st_row[i] = (int)(threadIdx.x + 256 * i) / (D / 8);
+    st_c8[i] = ((int)(threadIdx.x + 256 * i) % (D / 8)) * 8;
+  }
+  const int st_t = (int)threadIdx.x;
+  auto load_qtile = [&](int qt) {
+#pragma unroll
+    for (int i = 0; i < LPT; ++i) {
+      if (NCH % 256 && (int)threadIdx.x + 256 * i >= NCH) break;
+      const int qr = qt * QTT + st_row[i];
+      const int qr_c = qr < S ? qr : S - 1;
+      qreg[i] = *(const shortx8*)(q + qoff + (int64_t)qr_c * D + st_c8[i]);
+      dreg[i] = *(const shortx8*)(do_ + gbase + (int64_t)qr_c * g_sr + st_c8[i]);
+    }
+    if (st_t < QTT) {
+      const int rr = qt * QTT + st_t;
+      const int rr_c = rr < S ? rr : S - 1;
+      lse_reg = -lse[lseoff + rr_c] / scale;
+      dl_reg = -delta[lseoff + rr_c];
+    }
+  };
+  auto write_qtile = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < LPT; ++i) {
+      if (NCH % 256 && (int)threadIdx.x + 256 * i >= NCH) break;
+      *(shortx8*)(Q_lds + buf * QTT * DS + st_row[i] * DS + st_c8[i]) = qreg[i];
+      *(shortx8*)(dO_lds + buf * QTT * DS + st_row[i] * DS + st_c8[i]) = dreg[i];
+    }
+    if (st_t < QTT) {
+      lse_lds[buf * QTT + st_t] = lse_reg;
+      dl_lds[buf * QTT + st_t] = dl_reg;
+    }
+  };
+
+  load_qtile(qstart);
+  write_qtile(0);
+  __syncthreads();
+
+  for (int qt = qstart; qt < nQT2; ++qt) {
+    const int cur = (qt - qstart) & 1;
+    if (qt + 1 < nQT2) load_qtile(qt + 1);
+
+#pragma unroll
+    for (int hf = 0; hf < QTT / QT; ++hf) {
+      const int qbase = qt * QTT + hf * QT;
+      if (qbase + QT <= k0) continue;        // wave-uniform: every q < every key
+      const T* Qb = Q_lds + cur * QTT * DS + hf * QT * DS;
+      const T* dOb = dO_lds + cur * QTT * DS + hf * QT * DS;
+      const float* lse_b = lse_lds + cur * QTT + hf * QT;
+      const float* dl_b = dl_lds + cur * QTT + hf * QT;
+
+      // row constants into the accumulators: register r is q row
+      // 8*(r>>2) + 4*hi5 + (r&3)
+      floatx16 sc, dp;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const floatx4 l4 = *(const floatx4*)(lse_b + 8 * g + 4 * hi5);
+        const floatx4 d4 = *(const floatx4*)(dl_b + 8 * g + 4 * hi5);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { sc[4 * g + i] = l4[i]; dp[4 * g + i] = d4[i]; }
+      }
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) {
+        frag qa = *(const frag*)(Qb + lo32 * DS + kc * 16 + hi5 * 8);
+        sc = MF::mma(qa, k_frag[kc], sc);
+        frag doa = *(const frag*)(dOb + lo32 * DS + kc * 16 + hi5 * 8);
+        dp = MF::mma(doa, v_frag[kc], dp);
+      }
+      __builtin_amdgcn_s_setprio(0);
+
+      // P in sc, dS in dp.  Full tile: every q row >= every key of the wave
+      // and < S.  Otherwise (diagonal / last tile) mask per element; keys
+      // >= S need no mask: their dK/dV rows are never stored.
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sc[r] = exp2_fast(sc[r] * c2);
+      if (qbase < k0 + QT || qbase + QT > S) {   // diagonal / last tile only
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int qr = qbase + (r & 3) + 8 * (r >> 2) + 4 * hi5;
+          if (key > qr || qr >= S) sc[r] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] *= sc[r];
+      frag pf[2], dsf[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        pf[c] = pack_frag32<DT>(sc, c);
+        dsf[c] = pack_frag32<DT>(dp, c);
+      }
+
+      // ---- dV^T += dO^T P,  dK^T += Q^T dS ----
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          frag da = trread_afrag32<DT>(dOb, c * 16, mt * 32, DS, lane);
+          dv_acc[mt] = MF::mma(da, pf[c], dv_acc[mt]);
+          frag qa = trread_afrag32<DT>(Qb, c * 16, mt * 32, DS, lane);
+          dk_acc[mt] = MF::mma(qa, dsf[c], dk_acc[mt]);
+        }
+      __builtin_amdgcn_s_setprio(0);
+    }
+
+    if (qt + 1 < nQT2) write_qtile(cur ^ 1);
+    __syncthreads();
+  }
+
+  // lane key = lo32 owns its rows of dK^T / dV^T: d = mt*32 + 8g + 4*hi5 + 0..3
+  // (per q-head layout [B,Hq,S,D]; caller sums GQA groups)
+  if (key < S) {
+    const int64_t dvoff = dv_sb ? ((int64_t)b * dv_sb + (int64_t)h * dv_sh) : qoff;
+    const int64_t dv_rs = dv_sb ? dv_sr : (int64_t)D;
+    T* dkp = dk_out + qoff + (int64_t)key * D;
+    T* dvp = dv_out + dvoff + (int64_t)key * dv_rs;
+#pragma unroll
+    for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        store4<DT>(dkp + mt * 32 + 8 * g + 4 * hi5, dk_acc[mt], g, scale);
+        store4<DT>(dvp + mt * 32 + 8 * g + 4 * hi5, dv_acc[mt], g, 1.f);
+      }
   }
 }
 
@@ -1589,28 +1024,6 @@ static bool use_attn_v2() {
   static int cached = -1;
   if (cached < 0) {
     const char* e = getenv("DK_ATTN_V2");
-    cached = (e && e[0] == '1') ? 1 : 0;
-  }
-  return cached == 1;
-}
-
-// backward defaults to the 16x16 (v2) kernels: measured same-box A/B has
-// them ~7% faster than the 32x32 port (139 vs 148 TF); DK_ATTN_BWD_V3=1
-// opts into the v3 backward for future tuning.
-static bool use_bwd_split32() {
-  // split dv-only/dk-only 32x32 backward (A/B vs the fused 16x16 pair)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DK_ATTN_BWD_SPLIT32");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v != 0;
-}
-
-static bool use_bwd_v3() {
-  static int cached = -1;
-  if (cached < 0) {
-    const char* e = getenv("DK_ATTN_BWD_V3");
     cached = (e && e[0] == '1') ? 1 : 0;
   }
   return cached == 1;
@@ -1696,42 +1109,13 @@ static int launch_attn_bwd_dkdv(void* dk_o, void* dv_o, const void* do_, const v
                                 int64_t dv_sb, int64_t dv_sh, int64_t dv_sr,
                                 dkStream stream) {
   using T = typename DTraits<DT>::T;
-  constexpr int QT = 32, QS = QT + 8, DS = D + 8;
-  if (use_bwd_split32()) {
-    const int nKTs = (int)((S + 127) / 128);
-    const int grids = (int)(B * Hq * nKTs);
-    const size_t ldss = sizeof(T) * (4 * QT * DS + 4 * 32 * QS) + sizeof(float) * 4 * QT;
-    hipLaunchKernelGGL((attn_bwd_split32_kernel<DT, D, 0>), dim3(grids), dim3(256), ldss,
-                       (hipStream_t)stream, (T*)dv_o, (const T*)do_, (const T*)q,
-                       (const T*)k, (const T*)v, lse, delta, (int)B, (int)Hq,
-                       (int)Hkv, (int)S, scale, g_sb, g_sh, g_sr, v_sb, v_sh, v_sr,
-                       dv_sb, dv_sh, dv_sr);
-    DK_CHECK_LAUNCH();
-    hipLaunchKernelGGL((attn_bwd_split32_kernel<DT, D, 1>), dim3(grids), dim3(256), ldss,
-                       (hipStream_t)stream, (T*)dk_o, (const T*)do_, (const T*)q,
-                       (const T*)k, (const T*)v, lse, delta, (int)B, (int)Hq,
-                       (int)Hkv, (int)S, scale, g_sb, g_sh, g_sr, v_sb, v_sh, v_sr,
-                       0, 0, 0);
-    DK_CHECK_LAUNCH();
-    return 0;
-  }
-  if (use_bwd_v3() && v_sb == 0 && dv_sb == 0) {  // v3 port is contiguous-only
-    const int nKT3 = (int)((S + 127) / 128);
-    const int grid3 = (int)(B * Hq * nKT3);
-    const size_t lds3 = sizeof(T) * (4 * QT * DS + 2 * 4 * 32 * QS)
-                        + sizeof(float) * 4 * QT;
-    hipLaunchKernelGGL((attn_bwd_dkdv_v3_kernel<DT, D>), dim3(grid3), dim3(256), lds3,
-                       (hipStream_t)stream, (T*)dk_o, (T*)dv_o, (const T*)do_,
-                       (const T*)q, (const T*)k, (const T*)v, lse, delta,
-                       (int)B, (int)Hq, (int)Hkv, (int)S, scale, g_sb, g_sh, g_sr);
-    DK_CHECK_LAUNCH();
-    return 0;
-  }
-  const int nKT = (int)((S + 127) / 128);    // 8-wave WG: 128 keys
+  constexpr int QTT = 32, DS = D + 8;
+  // the epilogue stores 4 d-channels (8 B) per lane
+  if (((uintptr_t)dv_o & 7) || (dv_sb | dv_sh | dv_sr) & 3) return (int)hipErrorInvalidValue;
+  const int nKT = (int)((S + 127) / 128);    // 4 waves x 32 keys
   const int grid = (int)(B * Hq * nKT);
-  constexpr int QTT = 64;  // staged q tile (2 compute halves per barrier)
-  const size_t lds = sizeof(T) * (4 * QTT * DS + 2 * 8 * 16 * QS) + sizeof(float) * 4 * QTT;
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DT, D>), dim3(grid), dim3(512), lds,
+  const size_t lds = sizeof(T) * (4 * QTT * DS) + sizeof(float) * 4 * QTT;
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DT, D>), dim3(grid), dim3(256), lds,
                      (hipStream_t)stream, (T*)dk_o, (T*)dv_o, (const T*)do_,
                      (const T*)q, (const T*)k, (const T*)v, lse, delta,
                      (int)B, (int)Hq, (int)Hkv, (int)S, scale, g_sb, g_sh, g_sr,
@@ -1768,23 +1152,11 @@ static int launch_attn_bwd_dq(void* dq_o, const void* do_, const void* q, const 
                               int64_t v_sb, int64_t v_sh, int64_t v_sr,
                               dkStream stream) {
   using T = typename DTraits<DT>::T;
-  constexpr int KT = 32, KS = KT + 8, DS = D + 8;   // v3 tile constants
-  constexpr int KT2 = 64, KS2 = KT2 + 8;            // v2 8-wave tile constants
-  if (use_bwd_v3() && v_sb == 0) {  // v3 port is contiguous-only
-    const int nQT3 = (int)((S + 127) / 128);
-    const int grid3 = (int)(B * Hq * nQT3);
-    const size_t lds3 = sizeof(T) * (4 * KT * DS + 4 * 32 * KS);
-    hipLaunchKernelGGL((attn_bwd_dq_v3_kernel<DT, D>), dim3(grid3), dim3(256), lds3,
-                       (hipStream_t)stream, (T*)dq_o, (const T*)do_, (const T*)q,
-                       (const T*)k, (const T*)v, lse, delta, (int)B, (int)Hq,
-                       (int)Hkv, (int)S, scale, g_sb, g_sh, g_sr);
-    DK_CHECK_LAUNCH();
-    return 0;
-  }
-  const int nQT = (int)((S + 127) / 128);    // 8-wave WG: 128 q rows
+  constexpr int KT = 64, DS = D + 8;
+  const int nQT = (int)((S + 127) / 128);    // 4 waves x 32 q rows
   const int grid = (int)(B * Hq * nQT);
-  const size_t lds = sizeof(T) * (6 * KT2 * DS + 8 * 16 * KS2);  // 3-ring K+V
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<DT, D>), dim3(grid), dim3(512), lds,
+  const size_t lds = sizeof(T) * (4 * KT * DS);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<DT, D>), dim3(grid), dim3(256), lds,
                      (hipStream_t)stream, (T*)dq_o, (const T*)do_, (const T*)q,
                      (const T*)k, (const T*)v, lse, delta, (int)B, (int)Hq,
                      (int)Hkv, (int)S, scale, g_sb, g_sh, g_sr, v_sb, v_sh, v_sr);
